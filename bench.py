@@ -15,13 +15,19 @@ N > 1: one process per GPU, weak scaling (512 rows per GPU): every step trains O
 global batch of 512*N rows -- block r of global batch j is seeded by (j, r) and lives on
 rank r -- with one RCCL all-reduce of the flat fp32 buffer [gradient | loss scalars] per
 step and the Adam apply replicated.  `python bench.py --gpus N` starts its own N ranks
-(a parent that never touches the GPU spawns `python -m torch.distributed.run ...` and
-relays rank 0's line); under torchrun (WORLD_SIZE set) it is one of the ranks.
+(a parent that never touches the GPU spawns torch.distributed.run's launcher -- kept off the
+GPU too -- and relays rank 0's line); under torchrun (WORLD_SIZE set) it is one of the ranks.
 
-Timing: W untimed warm-up steps (at least one pass over the pool), then R repeats of
-EXACTLY K steps, each repeat bracketed by barrier + synchronize on both sides and reduced
-with MAX over ranks; `ms_per_step` / `value` come from the MEDIAN repeat (min / max are
-in the line), so the timed work is ~6 s (--timed-seconds) whatever K is.
+Timing: W untimed warm-up steps (at least one pass over the pool and 2 s), then R repeats (--repeats,
+default 1) of EXACTLY K steps, each repeat bracketed by barrier + synchronize on both sides and
+reduced with MAX over ranks; `ms_per_step` / `value` come from the MEDIAN repeat (min / max are
+in the line).  The timed steps are R x K: `--steps K` alone times K steps.  `--repeats 0` (or
+`--timed-seconds S` without --repeats) picks R so that the timed work lasts S seconds (default 7).
+
+`--dump-outputs DIR` writes what the timed path left after its last timed step -- parameters,
+TF-Adam slots, the step's scalars -- as DIR/<name>.npy (float32).  Inputs and the starting state
+are seeded, so with the same arguments two builds can be compared array for array (git ignores
+`bench_outputs/`, e.g. `--dump-outputs bench_outputs/<build>`).
 
 Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline`
 (dominant kernel, HIP-event timed), `roofline_eval` (scoring kernels), `cli_loop`
@@ -50,6 +56,7 @@ FP32_MFMA_PEAK_TF = 157.3  # dense fp32 MFMA peak (same guide)
 BF16X3_PEAK_TF = 2500.0 / 6.0  # fp32-equivalent ceiling of the bf16x3 arithmetic: dense bf16 peak / six partial products
 NORMALIZE_VALUE = 58.388599
 NOISE = float(os.environ.get("CFL_BENCH_NOISE", "0.3"))  # target-side noise of the planted positives
+WARMUP_MIN_S = 2.0     # least length of the untimed warm-up (main())
 
 
 def parse():
@@ -57,10 +64,12 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=50)
-    ap.add_argument('--repeats', type=int, default=0, help='timed repeats of the K-step region (0 = auto: >= 50 '
-                    'and enough for --timed-seconds of timed work)')
-    ap.add_argument('--timed-seconds', type=float, default=7.0, help='target length of the timed headline region (auto '
-                    'repeats): longer than the 5 s period of an external utilisation sampler')
+    ap.add_argument('--repeats', type=int, default=None, help='timed repeats of the K-step region, R x K timed steps in all '
+                    '(default 1, or 0 when --timed-seconds is given; 0 = auto: >= 50 and enough for --timed-seconds of timed work)')
+    ap.add_argument('--timed-seconds', type=float, default=None, help='target length of the timed headline region with auto '
+                    'repeats (default 7 s: longer than the 5 s period of an external utilisation sampler)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='', help='after the timed steps write the parameters, Adam slots '
+                    'and scalars of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)')
     ap.add_argument('--batch-size', type=int, default=512)
     ap.add_argument('--input-size', type=int, default=4096)
     ap.add_argument('--num-components', type=int, default=3)
@@ -102,7 +111,11 @@ def spawn_ranks(gpus, argv, key='"metric"', timeout=None, extra_env=None):
     with socket.socket() as s:
         s.bind(('127.0.0.1', 0))
         port = s.getsockname()[1]
-    cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(gpus),
+    # torch.distributed.run's main() with torch.cuda hidden from the launcher: it does no GPU work, but its launch config probes
+    # torch.cuda for NUMA-binding defaults, which opens the GPU -- one more process on a device whose limit of six processes the
+    # ranks of a job (and of the one-shot child job) already press against when they share one GPU
+    launcher = 'import sys, torch; torch.cuda.is_available = lambda: False; from torch.distributed.run import main; main(sys.argv[1:])'
+    cmd = [sys.executable, '-c', launcher, '--nnodes=1', '--nproc-per-node', str(gpus),
            '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + list(argv)
     env = dict(os.environ, MASTER_ADDR='127.0.0.1')
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT', 'GROUP_RANK', 'LOCAL_WORLD_SIZE', 'ROLE_RANK', 'ROLE_WORLD_SIZE',
@@ -958,6 +971,37 @@ def dp_form(args, eng, pool, device, fused_us):
             dist.destroy_process_group()
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6
+DUMP_WHOLE = 1 << 16
+
+
+def dump_outputs(path, eng):
+    """--dump-outputs: what a caller of the timed path (PairEngine.step) holds after the last timed step -- the parameters by
+    variable name (`param_outputs_W`, ..., `param_threshold`), the TF-Adam slots of each (`adam_m_*`, `adam_v_*`) and the step's
+    scalars in cfl.hipabi.SCALAR_NAMES order (`scalars`) -- as <path>/<name>.npy, float32.  Should they exceed DUMP_MAX_BYTES
+    together, every array of more than DUMP_WHOLE entries is replaced by the same fixed share of its flattened entries, picked
+    by RandomState(0); the smaller ones (biases, thresholds, scalars) are always written whole."""
+    import numpy as np
+    from cfl import hipabi as H
+    arrays = {}
+    for tag, buf in (('param', eng.theta), ('adam_m', eng.m), ('adam_v', eng.v)):
+        params, _, thr = H.unpack_theta(eng.shape, buf)        # (the bench's model has one head set: no `_dst` variables)
+        for name, a in params.items():
+            arrays['%s_%s' % (tag, name.replace('/', '_'))] = np.asarray(a, np.float32)
+        arrays[tag + '_threshold'] = np.array([thr], np.float32)
+    sc = eng.read_scalars()
+    arrays['scalars'] = np.array([sc[k] for k in H.SCALAR_NAMES], np.float32)
+    whole = 4096 * len(arrays) + sum(a.nbytes for a in arrays.values() if a.size <= DUMP_WHOLE)      # (+ .npy headers)
+    big = sum(a.nbytes for a in arrays.values() if a.size > DUMP_WHOLE)
+    keep = min(1.0, (DUMP_MAX_BYTES - whole) / float(big)) if big else 1.0
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if keep < 1.0 and a.size > DUMP_WHOLE:
+            idx = np.random.RandomState(0).choice(a.size, max(1, int(a.size * keep)), replace=False)
+            a = a.ravel()[np.sort(idx)]
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def _trace(msg):
     if os.environ.get('CFL_BENCH_TRACE'):
         print('[bench rank %s] %s' % (os.environ.get('RANK', '0'), msg), file=sys.stderr, flush=True)
@@ -1048,31 +1092,44 @@ def main():
     run(args.restore_steps, 0)
     snap = snapshot(eng)
     loss_at_restore = eng.read_scalars()['total']
-    warm = max(args.warmup, nb)          # every pool batch is touched before anything is timed
+    # warm-up: at least W steps and one pass over the pool (every batch is touched before anything is timed), and at least
+    # WARMUP_MIN_S of sustained steps: a single K = 20 window timed straight after a short burst read 2-10 % above the median
+    # of many repeats, 1-4 % after this warm-up (three runs each).  The timed repeats restore the training state, so the
+    # warm-up changes nothing they compute.
+    warm, t0 = max(args.warmup, nb), time.perf_counter()
     run(warm, args.restore_steps)
     sync_all()
-    _trace('warm-up done')
-    # short calibration (untimed for the result): how many repeats make --timed-seconds (6 s) of timed work -- longer than the
-    # 5 s period of an external utilisation sampler, so that it sees the GPU busy; the median repeat is what is reported
-    t0 = time.perf_counter()
-    run(args.steps, warm)
+    el = time.perf_counter() - t0
+    extra = int(np.ceil(max(0.0, WARMUP_MIN_S - el) * warm / el))
+    if world > 1:                        # (every step holds a collective: all ranks take rank 0's count)
+        xt = torch.tensor([extra], device=device, dtype=torch.int64)
+        dist.broadcast(xt, 0)
+        extra = int(xt.item())
+    run(extra, args.restore_steps + warm)
     sync_all()
-    est = max(time.perf_counter() - t0, 1e-6)
-    repeats = args.repeats if args.repeats > 0 else int(min(50000, max(50, np.ceil(args.timed_seconds / est))))
-    if world > 1:
-        rt = torch.tensor([repeats], device=device, dtype=torch.int64)
-        dist.broadcast(rt, 0)
-        repeats = int(rt.item())
+    _trace('warm-up done')
+    repeats = args.repeats if args.repeats is not None else (0 if args.timed_seconds else 1)
+    if repeats <= 0:
+        # --repeats 0: a short calibration (untimed for the result) picks how many repeats make --timed-seconds of timed work --
+        # longer than the 5 s period of an external utilisation sampler, so that it sees the GPU busy
+        t0 = time.perf_counter()
+        run(args.steps, args.restore_steps)
+        sync_all()
+        est = max(time.perf_counter() - t0, 1e-6)
+        repeats = int(min(50000, max(50, np.ceil((args.timed_seconds or 7.0) / est))))
+        if world > 1:
+            rt = torch.tensor([repeats], device=device, dtype=torch.int64)
+            dist.broadcast(rt, 0)
+            repeats = int(rt.item())
     times = []
-    pos = warm + args.steps
-    for _ in range(repeats):
+    for r in range(repeats):
         restore(eng, snap)               # (not timed: before the bracket's first barrier + synchronize)
         sync_all()
         t0 = time.perf_counter()
-        run(args.steps, pos)
+        # the first repeat continues the trajectory of the restored state: pool batches restore_steps, restore_steps + 1, ...
+        run(args.steps, args.restore_steps + r * args.steps)
         sync_all()
         times.append(time.perf_counter() - t0)
-        pos += args.steps
     tt = torch.tensor(times, device=device, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)       # slowest rank of every repeat
@@ -1080,6 +1137,10 @@ def main():
     elapsed = float(np.median(times))
     _trace('timed region done: %d repeats, median %.6f s' % (repeats, elapsed))
     scal = eng.read_scalars()
+    if args.dump_outputs:
+        eng.sync_state()                 # (collective under the one-shot exchange: its Adam slots are sharded over the ranks)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, eng)
 
     out = None
     if rank == 0:
@@ -1098,6 +1159,7 @@ def main():
             'dtype': 'f32',
             'data': 'synthetic',
             'repeats': repeats,
+            'timed_steps': repeats * args.steps,
             'ms_per_step_min': round(1e3 * float(times[0]) / args.steps, 5),
             'ms_per_step_max': round(1e3 * float(times[-1]) / args.steps, 5),
             'timed_s': round(float(times.sum()), 4),
